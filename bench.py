@@ -112,6 +112,8 @@ def make_step(model, cams, grads, wl, device, dp_grads=False):
         inflight.append(D.allreduce_sum_async(stats))
         if step.probe is not None:   # untimed passes only: look at the gradients before they are dropped
             step.probe(model)
+        if step.keep is not None:    # --dump-outputs: hold on to what a caller of the path receives (references, no copies)
+            step.keep.update(pkg=pkg, grads=[p.grad for p in params], viewspace_grad=pkg["viewspace_points"].grad)
         for p in params:
             p.grad = None
         pkg["viewspace_points"].grad = None
@@ -125,6 +127,7 @@ def make_step(model, cams, grads, wl, device, dp_grads=False):
     step.host_split = []
     step.n = 0
     step.probe = None
+    step.keep = None
     return step
 
 
@@ -209,6 +212,71 @@ def cpu_baseline(wl, full=False):
                 measured_seconds=round(t_pg + t_tiles + t_bwd, 2))
 
 
+DUMP_BUDGET_BYTES = 64_000_000 - (1 << 16)   # --dump-outputs: every .npy file together (the headers take the rest)
+
+
+def zero_by_construction(deform, tongue, coord=False):
+    """Dump names whose arrays the timed step makes zero whatever the build computes, so they say nothing about it:
+    viewspace_points (a zero tensor that only carries the 2D gradient, which is dumped), the coordinate images (not rendered
+    unless asked for: coord=False in the timed step), the tongue image of a scene without tongue Gaussians, and the gradients
+    of parameters the step does not read -- the per-camera offsets (the step passes cam_no=None, under which the deformation
+    shifts time by the mean of the NONZERO offsets: none at initialisation, as in the reference's scene/deformation.py), and,
+    in a workload without deformation, the whole deformation network and the per-Gaussian embeddings it alone reads."""
+    names = {"out_viewspace_points", "grad_deformation.offsets"}
+    if not coord:
+        names |= {"out_expected_coord", "out_median_coord"}
+    if not tongue:
+        names.add("out_tongue_mask")
+    if not deform:
+        names.add("grad_embedding")
+    return lambda n: n in names or (not deform and n.startswith("grad_deformation."))
+
+
+def dump_outputs(kept, model, path, deform=True):
+    """--dump-outputs: write what the last timed step computed -- render()'s tensors and the gradients its backward left on the
+    parameters and on viewspace_points, less what is zero by construction (zero_by_construction) -- as <path>/<name>.npy,
+    float32 (float64 stays float64).  An array too large for its share of the budget is replaced by a fixed sample: the flat
+    elements at sorted indices drawn without replacement by a generator seeded from the name, so two builds sample the same
+    elements."""
+    import zlib
+    import numpy as np
+    arrays = {}
+
+    def add(name, t):
+        if isinstance(t, torch.Tensor):
+            arrays[name] = t.detach()
+        elif isinstance(t, (tuple, list)):
+            for i, u in enumerate(t):
+                add("%s_%d" % (name, i), u)
+
+    for k, v in kept["pkg"].items():
+        add("out_" + k, v)
+    names = ["xyz", "scaling", "rotation", "opacity", "features_dc", "features_rest", "embedding"]
+    names += ["deformation." + n for n, _ in model._deformation.named_parameters()]
+    for n, g in zip(names, kept["grads"]):
+        add("grad_" + n, g)
+    add("grad_viewspace_points", kept["viewspace_grad"])
+    skip = zero_by_construction(deform, bool(model.tongue_class.any()))
+    arrays = {k: v for k, v in arrays.items() if not skip(k)}
+    # largest per-array element count that keeps the total within budget (arrays smaller than it are written whole)
+    size = {k: v.numel() * (8 if v.dtype == torch.float64 else 4) for k, v in arrays.items()}
+    cap = DUMP_BUDGET_BYTES
+    while sum(min(b, cap) for b in size.values()) > DUMP_BUDGET_BYTES:
+        cap = int(cap * 0.95)
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        a = v.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if size[k] > cap:
+            n = cap // a.itemsize
+            idx = np.sort(np.random.default_rng(zlib.crc32(k.encode())).choice(a.size, n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), a)
+        if not a.any():
+            log("dump: %s is all zero" % k)
+    return sorted(arrays)
+
+
 def log(*a):
     print("[bench]", *a, file=sys.stderr, flush=True)
 
@@ -228,10 +296,16 @@ def parse_args(argv=None):
     ap.add_argument("--train-only", action="store_true", help="skip the forward-only render-fps passes too, so that every launch of the run is a "
                     "training-step launch (for rocprofv3 --stats: its per-kernel averages then are the training step's)")
     ap.add_argument("--dp-grads", action="store_true", help="also all-reduce the gradients every step (data-parallel training; not the headline configuration)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (render() outputs, gradients) to DIR/<name>.npy, "
+                         "%d bytes at most in all (larger arrays: a fixed seeded sample of their elements)" % DUMP_BUDGET_BYTES)
     ap.add_argument("--rehearse-launcher", action="store_true",
                     help="NO GPU work and NO measurement: run the launcher / rendezvous / sharding / collectives / JSON plumbing "
                          "with a stub step (CPU, gloo) -- what tests/test_bench_launcher_cpu.py drives")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
+    return a
 
 
 def launch_ranks(a, argv):
@@ -287,12 +361,16 @@ def percentiles(v):
 def rehearse(a, D, emit):
     """Launcher rehearsal (no GPU, no measurement): every piece of the multi-rank harness around a stub step."""
     import torch.distributed as dist
-    rank, world, local = D.init()
+    # nothing here may initialise HIP: on a GPU box every rank would open the device.  So gloo by name (choosing by
+    # torch.cuda.is_available() initialises it), and a one-float host all-reduce as the barrier (torch's barrier() asks for the
+    # accelerator first, whatever the backend)
+    rank, world, local = D.init(backend="gloo")
+    host_barrier = lambda: D.allreduce_sum_(torch.zeros(1))
     wl = WORKLOADS[a.workload]
     n_items = wl["cams"] * wl["frames"]
     mine = D.shard_items(max(n_items, world), rank, world)
     inflight = []
-    D.barrier()
+    host_barrier()
     t0 = time.perf_counter()
     items = [D.visit_item(mine, k, wl["cams"], wl["frames"]) % n_items for k in range(a.steps)]   # the item schedule of the real path
     t_step = []
@@ -305,7 +383,7 @@ def rehearse(a, D, emit):
         t_step.append((time.perf_counter() - t1) * 1e3)
     while inflight:
         last = inflight.pop().wait()
-    D.barrier()
+    host_barrier()
     dt = D.max_over_ranks(time.perf_counter() - t0, "cpu")
     counts = torch.zeros(world); counts[rank] = a.steps
     D.allreduce_sum_(counts)
@@ -461,6 +539,8 @@ def main():
     step.host_split.clear()
     host_t = [t0]
     for k in range(a.steps):
+        if a.dump_outputs and k == a.steps - 1 and rank == 0:
+            step.keep = {}
         step(item_at(k))
         if (k + 1) % MARK_EVERY == 0:
             marks[(k + 1) // MARK_EVERY].record()
@@ -470,6 +550,10 @@ def main():
     dt = time.perf_counter() - t0
     gc.enable()
     n_malloc = (torch.cuda.memory_stats(device).get("num_device_alloc", 0) - n_malloc0) if torch.cuda.is_available() else 0
+    if step.keep is not None:
+        kept, step.keep = step.keep, None
+        log("dumped", len(dump_outputs(kept, model, a.dump_outputs, deform=wl["deform"])), "arrays to", a.dump_outputs)
+        del kept
     step_ms = [marks[k].elapsed_time(marks[k + 1]) / MARK_EVERY for k in range(len(marks) - 1)]
     slot_ms, slot_n = (ctypes.c_double * NS)(), (ctypes.c_int * NS)()
     L.ed3dgs_profile_end_slots(slot_ms, slot_n)
