@@ -489,6 +489,76 @@ int ed3dgs_rasterize_backward(
 size_t ed3dgs_integrate_point_bytes(int PN, int width, int height) { return integrate_point_bytes(PN, width, height); }
 size_t ed3dgs_integrate_workspace_bytes(int R, int width, int height) { return integrate_workspace_bytes(R, width, height); }
 
+int ed3dgs_integrate_view_prepare(
+    ed3dgs_alloc_fn geometry_alloc, void *geometry_user, ed3dgs_alloc_fn binning_alloc, void *binning_user,
+    ed3dgs_alloc_fn image_alloc, void *image_user, ed3dgs_alloc_fn workspace_alloc, void *workspace_user, int P, int D,
+    int M, const float *background, int width, int height, const float *means3D, const float *shs,
+    const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier, const float *rotations,
+    const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, const float *cam_pos, float tan_fovx,
+    float tan_fovy, float kernel_size, int prefiltered, float *out_color, float *accum_alpha, float *invraycov, int *radii,
+    unsigned char *condition, int debug, void *stream)
+{
+    (void)prefiltered;
+    hipStream_t s = (hipStream_t)stream;
+    if (P <= 0 || width <= 0 || height <= 0) { set_error("ed3dgs_integrate_view_prepare: bad P/width/height"); return ED3DGS_ERR_INVALID; }
+    if (!geometry_alloc || !binning_alloc || !image_alloc || !workspace_alloc) { set_error("ed3dgs_integrate_view_prepare: null allocator"); return ED3DGS_ERR_INVALID; }
+    if (!means3D || !opacities || !viewmatrix || !projmatrix || !cam_pos || !background || !radii || !out_color ||
+        !accum_alpha || !invraycov || !condition) {
+        set_error("ed3dgs_integrate_view_prepare: null required pointer"); return ED3DGS_ERR_INVALID;
+    }
+    if (!colors_precomp && !shs) { set_error("For non-RGB, provide precomputed Gaussian colors!"); return ED3DGS_ERR_INVALID; }   // CR/rasterizer_impl.cu:643-646
+    if (!cov3D_precomp && (!scales || !rotations)) { set_error("ed3dgs_integrate_view_prepare: need scales+rotations or cov3D_precomp"); return ED3DGS_ERR_INVALID; }
+    if (shs && !colors_precomp && (M < (D + 1) * (D + 1) || D < 0 || D > 3)) { set_error("ed3dgs_integrate_view_prepare: SH degree/coeff mismatch"); return ED3DGS_ERR_INVALID; }
+    StageCheck ok{debug != 0, s};
+    GeometryState geom;
+    ImageState img;
+    BinningState bin;
+    const int R = bin_gaussians(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M,
+                                width, height, means3D, shs, colors_precomp, opacities, nullptr, scales, scale_modifier,
+                                rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, kernel_size,
+                                radii, invraycov, condition, ok, s, geom, img, bin);
+    if (R < 0) return R;
+    char *wchunk = workspace_alloc(workspace_user, ed3dgs_integrate_workspace_bytes(R, width, height));
+    if (!wchunk) { set_error("integrate: view workspace allocation failed"); return ED3DGS_ERR_ALLOC; }
+    launch_integrate_pixels(R, width, height, img.ranges, bin.point_list, geom.rec, background, wchunk, out_color, accum_alpha, s);
+    if (!ok("integrate pixels")) return ED3DGS_ERR_HIP;
+    return R;
+}
+
+int ed3dgs_integrate_view_probe(
+    int PN, int P, int R, int width, int height, const char *geometry_buffer, const char *binning_buffer,
+    const char *image_buffer, const char *workspace, ed3dgs_alloc_fn point_alloc, void *point_user, const float *points3D,
+    const float *viewmatrix, float tan_fovx, float tan_fovy, const float *invraycov, const unsigned char *condition,
+    const float *out_color, float *point_count, float *out_alpha_integrated, float *out_color_integrated,
+    float *out_coordinate2d, float *out_sdf, int debug, void *stream)
+{
+    hipStream_t s = (hipStream_t)stream;
+    if (PN < 0 || P <= 0 || R < 0 || width <= 0 || height <= 0) { set_error("ed3dgs_integrate_view_probe: bad PN/P/R/width/height"); return ED3DGS_ERR_INVALID; }
+    if (!point_alloc) { set_error("ed3dgs_integrate_view_probe: null allocator"); return ED3DGS_ERR_INVALID; }
+    if (PN == 0) return 0;
+    if (!geometry_buffer || (!binning_buffer && R > 0) || !image_buffer || !workspace || !points3D || !viewmatrix || !invraycov ||
+        !condition || !out_color || !out_alpha_integrated || !out_color_integrated || !out_coordinate2d || !out_sdf) {
+        set_error("ed3dgs_integrate_view_probe: null required pointer"); return ED3DGS_ERR_INVALID;
+    }
+    StageCheck ok{debug != 0, s};
+    char *gc = (char *)geometry_buffer, *bc = (char *)binning_buffer, *ic = (char *)image_buffer;
+    GeometryState geom = GeometryState::from_chunk(gc, P);
+    BinningState bin = BinningState::from_chunk(bc, R);
+    ImageState img = ImageState::from_chunk(ic, (size_t)width * height, tiles_of(width, height));
+    const float focal_y = height / (2.0f * tan_fovy);
+    const float focal_x = width / (2.0f * tan_fovx);
+    char *pchunk = point_alloc(point_user, ed3dgs_integrate_point_bytes(PN, width, height));
+    if (!pchunk) { set_error("integrate: point-state allocation failed"); return ED3DGS_ERR_ALLOC; }
+    const int point_bits = (int)higher_msb((uint32_t)tiles_of(width, height) + 1);
+    if (!launch_integrate_points(PN, R, width, height, points3D, viewmatrix, focal_x, focal_y, img.ranges, bin.point_list,
+                                 geom.rec, invraycov, condition, pchunk, workspace, out_color, point_count,
+                                 out_alpha_integrated, out_color_integrated, out_coordinate2d, out_sdf, point_bits, s))
+        return ED3DGS_ERR_HIP;
+    if (!ok("integrate points")) return ED3DGS_ERR_HIP;
+    return 0;
+}
+
+// prepare + probe: one view, one point set (the two halves read and write exactly what the single call did)
 int ed3dgs_integrate(
     ed3dgs_alloc_fn geometry_alloc, void *geometry_user, ed3dgs_alloc_fn binning_alloc, void *binning_user,
     ed3dgs_alloc_fn image_alloc, void *image_user, ed3dgs_alloc_fn point_alloc, void *point_user,
@@ -500,38 +570,29 @@ int ed3dgs_integrate(
     float *out_alpha_integrated, float *out_color_integrated, float *out_coordinate2d, float *out_sdf,
     unsigned char *condition, int debug, void *stream)
 {
-    (void)prefiltered;
-    hipStream_t s = (hipStream_t)stream;
     if (P < 0 || PN < 0 || width <= 0 || height <= 0) { set_error("ed3dgs_integrate: bad P/PN/width/height"); return ED3DGS_ERR_INVALID; }
     if (!geometry_alloc || !binning_alloc || !image_alloc || !point_alloc || !point_binning_alloc) { set_error("ed3dgs_integrate: null allocator"); return ED3DGS_ERR_INVALID; }
     if (P == 0 || PN == 0) return 0;  // DGR/rasterize_points.cu:345
-    if (!points3D || !means3D || !opacities || !viewmatrix || !projmatrix || !cam_pos || !background || !radii || !out_color ||
-        !accum_alpha || !invraycov || !out_alpha_integrated || !out_color_integrated || !out_coordinate2d || !out_sdf || !condition) {
+    if (!points3D || !out_alpha_integrated || !out_color_integrated || !out_coordinate2d || !out_sdf) {
         set_error("ed3dgs_integrate: null required pointer"); return ED3DGS_ERR_INVALID;
     }
-    if (!colors_precomp && !shs) { set_error("For non-RGB, provide precomputed Gaussian colors!"); return ED3DGS_ERR_INVALID; }   // CR/rasterizer_impl.cu:643-646
-    if (!cov3D_precomp && (!scales || !rotations)) { set_error("ed3dgs_integrate: need scales+rotations or cov3D_precomp"); return ED3DGS_ERR_INVALID; }
-    if (shs && !colors_precomp && (M < (D + 1) * (D + 1) || D < 0 || D > 3)) { set_error("ed3dgs_integrate: SH degree/coeff mismatch"); return ED3DGS_ERR_INVALID; }
-    StageCheck ok{debug != 0, s};
-    const float focal_y = height / (2.0f * tan_fovy);
-    const float focal_x = width / (2.0f * tan_fovx);
-    GeometryState geom;
-    ImageState img;
-    BinningState bin;
-    const int R = bin_gaussians(geometry_alloc, geometry_user, binning_alloc, binning_user, image_alloc, image_user, P, D, M,
-                                width, height, means3D, shs, colors_precomp, opacities, nullptr, scales, scale_modifier,
-                                rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy, kernel_size,
-                                radii, invraycov, condition, ok, s, geom, img, bin);
+    // the allocators hand out the chunks; remember them for the probe
+    struct Tap { ed3dgs_alloc_fn fn; void *user; char *got; };
+    Tap taps[4] = {{geometry_alloc, geometry_user, nullptr}, {binning_alloc, binning_user, nullptr},
+                   {image_alloc, image_user, nullptr}, {point_binning_alloc, point_binning_user, nullptr}};
+    auto tap = [](void *u, size_t n) -> char * { Tap *t = (Tap *)u; return t->got = t->fn(t->user, n); };
+    const int R = ed3dgs_integrate_view_prepare(tap, &taps[0], tap, &taps[1], tap, &taps[2], tap, &taps[3], P, D, M, background,
+                                                width, height, means3D, shs, colors_precomp, opacities, scales, scale_modifier,
+                                                rotations, cov3D_precomp, viewmatrix, projmatrix, cam_pos, tan_fovx, tan_fovy,
+                                                kernel_size, prefiltered, out_color, accum_alpha, invraycov, radii, condition,
+                                                debug, stream);
     if (R < 0) return R;
-    char *pchunk = point_alloc(point_user, ed3dgs_integrate_point_bytes(PN, width, height));
-    char *wchunk = point_binning_alloc(point_binning_user, ed3dgs_integrate_workspace_bytes(R, width, height));
-    if (!pchunk || !wchunk) { set_error("integrate: point-state allocation failed"); return ED3DGS_ERR_ALLOC; }
-    const int point_bits = (int)higher_msb((uint32_t)tiles_of(width, height) + 1);
-    if (!launch_integrate(PN, R, width, height, points3D, viewmatrix, focal_x, focal_y, img.ranges, bin.point_list, geom.rec,
-                          invraycov, condition, background, pchunk, wchunk, out_color, accum_alpha, out_alpha_integrated,
-                          out_color_integrated, out_coordinate2d, out_sdf, point_bits, s)) return ED3DGS_ERR_HIP;
-    if (!ok("integrate")) return ED3DGS_ERR_HIP;
-    return R;
+    const size_t HW = (size_t)width * height;
+    const int rc = ed3dgs_integrate_view_probe(PN, P, R, width, height, taps[0].got, taps[1].got, taps[2].got, taps[3].got,
+                                               point_alloc, point_user, points3D, viewmatrix, tan_fovx, tan_fovy, invraycov,
+                                               condition, out_color, out_color + 8 * HW, out_alpha_integrated,
+                                               out_color_integrated, out_coordinate2d, out_sdf, debug, stream);
+    return rc < 0 ? rc : R;
 }
 
 int ed3dgs_profile_begin(int max_samples)

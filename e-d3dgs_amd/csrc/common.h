@@ -156,11 +156,14 @@ bool launch_activations_backward(int P, const float *s_log, const float *rot_raw
 // integrate.hip (point integration: K12-K14)
 size_t integrate_point_bytes(int PN, int width, int height);
 size_t integrate_workspace_bytes(int R, int width, int height);
-bool launch_integrate(int PN, int R, int W, int H, const float *points3D, const float *view, float focal_x, float focal_y,
-                      const uint32_t *ranges, const uint32_t *point_list, const float *rec, const float *invraycov,
-                      const uint8_t *condition, const float *bg, char *point_chunk, char *work_chunk, float *out_color,
-                      float *accum_alpha, float *out_alpha_integrated, float *out_color_integrated,
-                      float *out_coordinate2d, float *out_sdf, int point_end_bit, hipStream_t s);
+void launch_integrate_pixels(int R, int W, int H, const uint32_t *ranges, const uint32_t *point_list, const float *rec,
+                             const float *bg, char *work_chunk, float *out_color, float *accum_alpha, hipStream_t s);
+bool launch_integrate_points(int PN, int R, int W, int H, const float *points3D, const float *view, float focal_x,
+                             float focal_y, const uint32_t *ranges, const uint32_t *point_list, const float *rec,
+                             const float *invraycov, const uint8_t *condition, char *point_chunk, const char *work_chunk,
+                             const float *color, float *point_count, float *out_alpha_integrated,
+                             float *out_color_integrated, float *out_coordinate2d, float *out_sdf, int point_end_bit,
+                             hipStream_t s);
 void launch_preprocess_backward(int P, int D, int M, const float *means, const int *radii, const float *shs,
                                 const float *scales, const float *rotations, float scale_modifier,
                                 const float *cov3D_precomp, const float *view, const float *proj, const float *campos,

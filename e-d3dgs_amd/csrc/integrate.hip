@@ -155,7 +155,8 @@ __global__ void __launch_bounds__(256) integrate_points_kernel(
     const uint32_t *__restrict__ point_list, const uint32_t *__restrict__ qpoint_list, const float *__restrict__ rec,
     const float *__restrict__ invraycov, const uint8_t *__restrict__ condition, const float2 *__restrict__ points2D,
     const float *__restrict__ pdepths, const uint32_t *__restrict__ last_contrib, const float *__restrict__ pixaux,
-    const unsigned long long *__restrict__ used, float *__restrict__ out_color, float *__restrict__ out_alpha_integrated,
+    const unsigned long long *__restrict__ used, const float *__restrict__ color, float *__restrict__ point_count,
+    float *__restrict__ out_alpha_integrated,
     float *__restrict__ out_color_integrated, float *__restrict__ out_coordinate2d, float *__restrict__ out_sdf)
 {
     constexpr int CH = 128;   // list entries per staging round
@@ -235,9 +236,9 @@ __global__ void __launch_bounds__(256) integrate_points_kernel(
         }
         if (valid) {
             out_alpha_integrated[pid] = acc;
-            out_color_integrated[3 * (size_t)pid + 0] = out_color[0 * HW + pix];
-            out_color_integrated[3 * (size_t)pid + 1] = out_color[1 * HW + pix];
-            out_color_integrated[3 * (size_t)pid + 2] = out_color[2 * HW + pix];
+            out_color_integrated[3 * (size_t)pid + 0] = color[0 * HW + pix];
+            out_color_integrated[3 * (size_t)pid + 1] = color[1 * HW + pix];
+            out_color_integrated[3 * (size_t)pid + 2] = color[2 * HW + pix];
             out_coordinate2d[2 * (size_t)pid] = xy.x;
             out_coordinate2d[2 * (size_t)pid + 1] = xy.y;
             if (pdepth > 0) {
@@ -245,7 +246,9 @@ __global__ void __launch_bounds__(256) integrate_points_kernel(
                 const float dx = ax[3] - xy.x, dy = ax[4] - xy.y;
                 out_sdf[pid] = (ax[0] + (ax[1] * dx + ax[2] * dy)) - pdepth;
             }
-            atomicAdd(out_color + 8 * HW + pix, 1.0f);   // DISTORTION_OFFSET: number of points of the pixel
+            // DISTORTION_OFFSET: number of points of the pixel; skipped by the view-cache probe (null), whose repeated probes
+            // would otherwise accumulate into the cached image
+            if (point_count) atomicAdd(point_count + pix, 1.0f);
         }
     }
 }
@@ -285,6 +288,23 @@ static size_t carve_points(int PN, size_t T, char *base, IntegratePointState *ou
     return (size_t)(p - base) + 128;
 }
 
+struct IntegrateView {
+    unsigned long long *used;   // [R, 4] ballot words: which pixels of each wave a list entry touched
+    uint32_t *last_contrib;     // [H, W]
+    float *pixaux;              // [H, W, 8] median contributor's record
+};
+
+static IntegrateView integrate_view(int R, int W, int H, char *work_chunk)
+{
+    const size_t HW = (size_t)W * H;
+    IntegrateView v;
+    char *wp = work_chunk;
+    obtain(wp, v.used, (size_t)(R > 0 ? R : 0) * 4, 128);
+    obtain(wp, v.last_contrib, HW, 128);
+    obtain(wp, v.pixaux, HW * 8, 128);
+    return v;
+}
+
 size_t integrate_point_bytes(int PN, int width, int height)
 {
     const size_t T = (size_t)((width + TILE - 1) / TILE) * ((height + TILE - 1) / TILE);
@@ -297,24 +317,31 @@ size_t integrate_workspace_bytes(int R, int width, int height)
     return (size_t)(R > 0 ? R : 0) * 32 + HW * 4 + HW * 32 + 512;
 }
 
-bool launch_integrate(int PN, int R, int W, int H, const float *points3D, const float *view, float focal_x, float focal_y,
-                      const uint32_t *ranges, const uint32_t *point_list, const float *rec, const float *invraycov,
-                      const uint8_t *condition, const float *bg, char *point_chunk, char *work_chunk, float *out_color,
-                      float *accum_alpha, float *out_alpha_integrated, float *out_color_integrated,
-                      float *out_coordinate2d, float *out_sdf, int point_end_bit, hipStream_t s)
+// The per-view half (K14's first loop): reads nothing of the query points, so the view cache runs it once per view.
+// `work_chunk` (ed3dgs_integrate_workspace_bytes(R, W, H)) keeps the ballot words, last contributors and median records.
+void launch_integrate_pixels(int R, int W, int H, const uint32_t *ranges, const uint32_t *point_list, const float *rec,
+                             const float *bg, char *work_chunk, float *out_color, float *accum_alpha, hipStream_t s)
 {
     const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-    const size_t T = (size_t)gx * gy, HW = (size_t)W * H;
+    IntegrateView v = integrate_view(R, W, H, work_chunk);
+    hipLaunchKernelGGL(integrate_pixels_kernel, dim3(gx, gy), dim3(256), 0, s, W, H, ranges, point_list, rec, bg, out_color,
+                       accum_alpha, v.last_contrib, v.pixaux, v.used);
+}
+
+// The per-point-set half: K12, K13 and K14's second loop against a prepared view.  `point_count` (out_color channel 8)
+// may be null.
+bool launch_integrate_points(int PN, int R, int W, int H, const float *points3D, const float *view, float focal_x,
+                             float focal_y, const uint32_t *ranges, const uint32_t *point_list, const float *rec,
+                             const float *invraycov, const uint8_t *condition, char *point_chunk, const char *work_chunk,
+                             const float *color, float *point_count, float *out_alpha_integrated,
+                             float *out_color_integrated, float *out_coordinate2d, float *out_sdf, int point_end_bit,
+                             hipStream_t s)
+{
+    const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+    const size_t T = (size_t)gx * gy;
     IntegratePointState ps;
     carve_points(PN, T, (char *)(((uintptr_t)point_chunk + 127) & ~(uintptr_t)127), &ps);
-    char *wp = work_chunk;
-    unsigned long long *used = nullptr;
-    uint32_t *last_contrib = nullptr;
-    float *pixaux = nullptr;
-    obtain(wp, used, (size_t)(R > 0 ? R : 0) * 4, 128);
-    obtain(wp, last_contrib, HW, 128);
-    obtain(wp, pixaux, HW * 8, 128);
-
+    IntegrateView v = integrate_view(R, W, H, (char *)work_chunk);
     hipLaunchKernelGGL(integrate_points_preprocess_kernel, dim3((PN + 255) / 256), dim3(256), 0, s, PN, points3D, view, W, H,
                        focal_x, focal_y, gx, gy, ps.points2D, ps.depths, ps.keys, ps.ids);
     size_t bytes = ps.sort_bytes;
@@ -322,11 +349,9 @@ bool launch_integrate(int PN, int R, int W, int H, const float *points3D, const 
                                                       point_end_bit, s), "integrate: sort points")) return false;
     if (!check_hip(hipMemsetAsync(ps.ranges, 0, (T + 1) * 2 * sizeof(uint32_t), s), "integrate: memset point ranges")) return false;
     launch_identify_tile_ranges(PN, ps.keys_sorted, ps.ranges, s);
-    hipLaunchKernelGGL(integrate_pixels_kernel, dim3(gx, gy), dim3(256), 0, s, W, H, ranges, point_list, rec, bg, out_color,
-                       accum_alpha, last_contrib, pixaux, used);
     hipLaunchKernelGGL(integrate_points_kernel, dim3(gx, gy), dim3(256), 0, s, W, H, ranges, ps.ranges, point_list,
-                       ps.ids_sorted, rec, invraycov, condition, ps.points2D, ps.depths, last_contrib, pixaux, used,
-                       out_color, out_alpha_integrated, out_color_integrated, out_coordinate2d, out_sdf);
+                       ps.ids_sorted, rec, invraycov, condition, ps.points2D, ps.depths, v.last_contrib, v.pixaux, v.used,
+                       color, point_count, out_alpha_integrated, out_color_integrated, out_coordinate2d, out_sdf);
     return check_hip(hipGetLastError(), "integrate");
 }
 

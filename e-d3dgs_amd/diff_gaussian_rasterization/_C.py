@@ -261,6 +261,89 @@ def integrate_gaussians_to_points(background, points3D, means3D, colors, opacity
             binning.t, img.t)
 
 
+class IntegrateView:
+    """One view prepared for repeated point probes (ed3dgs_integrate_view_prepare / _probe of include/ed3dgs.h).  Holds the
+    geometry, binning and image states, the view workspace and the per-view arrays; `probe` integrates a point set
+    against them without re-running the preprocess, the binning or the per-pixel pass."""
+
+    def __init__(self, background, means3D, colors, opacity, scales, rotations, scale_modifier, cov3D_precomp, viewmatrix,
+                 projmatrix, tan_fovx, tan_fovy, image_height, image_width, sh, degree, campos, prefiltered, debug):
+        if means3D.dim() != 2 or means3D.size(1) != 3 or means3D.size(0) == 0:
+            raise RuntimeError("means3D must have dimensions (num_points, 3) with num_points > 0")
+        L = _lib.lib()
+        P = means3D.size(0)
+        H, W = _num(image_height, int), _num(image_width, int)
+        dev = means3D.device
+        means3D = _f32c(means3D, "means3D")
+        colors = _f32c(colors, "colors_precomp"); opacity = _f32c(opacity, "opacities"); scales = _f32c(scales, "scales")
+        rotations = _f32c(rotations, "rotations"); cov3D_precomp = _f32c(cov3D_precomp, "cov3D_precomp")
+        sh = _f32c(sh, "sh"); background = _f32c(background, "bg")
+        self.viewmatrix = _f32c(viewmatrix, "viewmatrix")
+        projmatrix = _f32c(projmatrix, "projmatrix"); campos = _f32c(campos, "campos")
+        fopt = dict(dtype=torch.float32, device=dev)
+        self.out_color = torch.zeros((9, H, W), **fopt)
+        self.accum_alpha = torch.zeros((1, H, W), **fopt)
+        self.radii = torch.zeros((P,), dtype=torch.int32, device=dev)
+        self.invraycov = torch.zeros((P, 6), **fopt)
+        self.condition = torch.zeros((P,), dtype=torch.uint8, device=dev)
+        self.bufs = [_Grow(dev) for _ in range(4)]   # geometry, binning, image, view workspace
+        self.stream = torch.cuda.current_stream(dev)   # the prepare's stream: probes on another stream wait for it
+        self.P, self.H, self.W, self.dev = P, H, W, dev
+        self.tan_fovx, self.tan_fovy, self.debug = _num(tan_fovx, float), _num(tan_fovy, float), bool(debug)
+        M = sh.size(1) if sh.numel() else 0
+        g, b, i, w = self.bufs
+        R = L.ed3dgs_integrate_view_prepare(
+            g.cb, None, b.cb, None, i.cb, None, w.cb, None, C.c_int(P), C.c_int(_num(degree, int)), C.c_int(M),
+            _ptr(background), C.c_int(W), C.c_int(H), _ptr(means3D), _ptr(sh), _ptr(colors), _ptr(opacity), _ptr(scales),
+            C.c_float(_num(scale_modifier, float)), _ptr(rotations), _ptr(cov3D_precomp), _ptr(self.viewmatrix),
+            _ptr(projmatrix), _ptr(campos), C.c_float(self.tan_fovx), C.c_float(self.tan_fovy), C.c_float(0.0),
+            C.c_int(bool(prefiltered)), _ptr(self.out_color), _ptr(self.accum_alpha), _ptr(self.invraycov),
+            _ptr(self.radii), _ptr(self.condition), C.c_int(self.debug), _stream())
+        if R < 0:
+            raise RuntimeError(_lib.last_error())
+        self.R = R
+
+    @property
+    def nbytes(self):
+        """Device bytes this view keeps: the four chunks (as sized by ed3dgs_geometry_bytes, _binning_bytes, _image_bytes and
+        _integrate_workspace_bytes) plus the per-view arrays."""
+        held = [b.t for b in self.bufs] + [self.out_color, self.accum_alpha, self.radii, self.invraycov, self.condition,
+                                           self.viewmatrix]
+        return sum(t.numel() * t.element_size() for t in held)
+
+    def probe(self, points3D):
+        """(alpha_integrated [PN], color_integrated [PN,3], coordinate2d [PN,2], sdf [PN]) of the points against this view,
+        initialised as IntegrateGaussiansToPointsCUDA does.  Enqueued on the current stream, after the prepare's work.  The cached image's channel 8 (points per pixel) is not
+        touched."""
+        if points3D.dim() != 2 or points3D.size(1) != 3:
+            raise RuntimeError("points3D must have dimensions (num_points, 3)")
+        points3D = _f32c(points3D, "points3D")
+        PN = points3D.size(0)
+        cur = torch.cuda.current_stream(self.dev)
+        if cur != self.stream:
+            # order this probe after the prepare, and keep the cached state's memory from being reused by the prepare's
+            # stream while the probe may still read it
+            cur.wait_stream(self.stream)
+            for t in [b.t for b in self.bufs] + [self.out_color, self.invraycov, self.condition, self.viewmatrix]:
+                t.record_stream(cur)
+        fopt = dict(dtype=torch.float32, device=self.dev)
+        alpha = torch.ones((PN,), **fopt)
+        color = torch.zeros((PN, 3), **fopt)
+        coord = torch.zeros((PN, 2), **fopt)
+        sdf = torch.full((PN,), -1000.0, **fopt)
+        if PN:
+            g, b, i, w = self.bufs
+            pts = _Grow(self.dev)
+            rc = _lib.lib().ed3dgs_integrate_view_probe(
+                C.c_int(PN), C.c_int(self.P), C.c_int(self.R), C.c_int(self.W), C.c_int(self.H), _ptr(g.t), _ptr(b.t),
+                _ptr(i.t), _ptr(w.t), pts.cb, None, _ptr(points3D), _ptr(self.viewmatrix), C.c_float(self.tan_fovx),
+                C.c_float(self.tan_fovy), _ptr(self.invraycov), _ptr(self.condition), _ptr(self.out_color), None,
+                _ptr(alpha), _ptr(color), _ptr(coord), _ptr(sdf), C.c_int(self.debug), _stream())
+            if rc < 0:
+                raise RuntimeError(_lib.last_error())
+        return alpha, color, coord, sdf
+
+
 def n_contrib_view(P, H, W, R, geomBuffer, imageBuffer):
     """(2,H,W) int32 GPU tensor aliasing the image state's n_contrib planes (last / median contributor)."""
     L = _lib.lib()

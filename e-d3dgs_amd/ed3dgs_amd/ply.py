@@ -85,3 +85,39 @@ def attribute_names(n_dc, n_rest, n_scale, n_rot, n_embedding, exclude_filter=Fa
     if not exclude_filter:
         l.append("filter_3D")
     return l
+
+
+def read_mesh(path):
+    """(vertices [V,3] float32, faces [F,3] int64) of a binary little-endian triangle mesh whose vertex element holds
+    float x, y, z and whose face element holds one `list uchar int` property (the layout mesh.write_mesh_ply writes)."""
+    with open(path, "rb") as f:
+        if f.readline().strip() != b"ply":
+            raise ValueError("%s: not a PLY file" % path)
+        fmt, elems = None, []
+        while True:
+            line = f.readline()
+            if not line:
+                raise ValueError("%s: PLY header is not terminated" % path)
+            tok = line.decode("ascii").split()
+            if not tok or tok[0] in ("comment", "obj_info"):
+                continue
+            if tok[0] == "format":
+                fmt = tok[1]
+            elif tok[0] == "element":
+                elems.append((tok[1], int(tok[2]), []))
+            elif tok[0] == "property":
+                elems[-1][2].append(tuple(tok[1:]))
+            elif tok[0] == "end_header":
+                break
+        if fmt != "binary_little_endian" or [e[0] for e in elems] != ["vertex", "face"]:
+            raise ValueError("%s: expected a binary little-endian vertex + face mesh" % path)
+        (_, nv, vp), (_, nf, fp) = elems
+        if [p[-1] for p in vp] != ["x", "y", "z"] or any(p[0] not in ("float", "float32") for p in vp):
+            raise ValueError("%s: vertex element must be float x, y, z" % path)
+        if len(fp) != 1 or fp[0][:3] not in (("list", "uchar", "int"), ("list", "uint8", "int32")):
+            raise ValueError("%s: face element must be one `list uchar int` property" % path)
+        v = np.frombuffer(f.read(nv * 12), dtype="<f4", count=nv * 3).reshape(nv, 3).astype(np.float32)
+        body = np.frombuffer(f.read(nf * 13), dtype=[("n", "u1"), ("i", "<i4", (3,))], count=nf)
+        if nf and (body["n"] != 3).any():
+            raise ValueError("%s: only triangles are supported" % path)
+    return v, body["i"].astype(np.int64).reshape(nf, 3)

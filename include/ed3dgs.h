@@ -200,6 +200,61 @@ int ed3dgs_integrate(
     unsigned char *condition, int debug, void *stream);
 
 /*
+ * The view cache of the mesh extraction (mesh_extract_tetrahedra.py calls integrate 9 x V times per timestep with the
+ * same Gaussians and views; only the query points change).  ed3dgs_integrate is exactly prepare followed by probe.
+ *
+ * ed3dgs_integrate_view_prepare: preprocess, binning and K14's per-pixel loop of one view.  Arguments as
+ * ed3dgs_integrate without the points; P > 0.  Fills out_color channels 0-7, accum_alpha, invraycov, radii and
+ * condition (caller-filled as for ed3dgs_integrate) and returns R (>= 0) or an error code.  The four allocators are
+ * asked for the geometry, binning and image states and the view workspace (ed3dgs_integrate_workspace_bytes(R, W, H));
+ * the caller keeps all four chunks, and the filled arrays, unchanged for as long as it probes the view.
+ *
+ * ed3dgs_integrate_view_probe: K12, K13 and K14's per-point loop of PN points against a prepared view.  The four chunks
+ * are the pointers the prepare's allocators returned; out_color is the prepared [9,H,W] image (channels 0-2 read).
+ * point_count (channel 8 of a [9,H,W] image, += 1 per projected point) may be null: the atomic is then skipped, so
+ * repeated probes leave the cached image unchanged.  Outputs caller-filled as for ed3dgs_integrate: out_alpha_integrated
+ * [PN] ones, out_color_integrated [PN,3] zeros, out_coordinate2d [PN,2] zeros, out_sdf [PN] -1000.  `point_alloc` is
+ * asked for ed3dgs_integrate_point_bytes(PN, W, H) bytes.  Returns 0 or an error code.
+ */
+int ed3dgs_integrate_view_prepare(
+    ed3dgs_alloc_fn geometry_alloc, void *geometry_user, ed3dgs_alloc_fn binning_alloc, void *binning_user,
+    ed3dgs_alloc_fn image_alloc, void *image_user, ed3dgs_alloc_fn workspace_alloc, void *workspace_user, int P, int D,
+    int M, const float *background, int width, int height, const float *means3D, const float *shs,
+    const float *colors_precomp, const float *opacities, const float *scales, float scale_modifier, const float *rotations,
+    const float *cov3D_precomp, const float *viewmatrix, const float *projmatrix, const float *cam_pos, float tan_fovx,
+    float tan_fovy, float kernel_size, int prefiltered, float *out_color, float *accum_alpha, float *invraycov, int *radii,
+    unsigned char *condition, int debug, void *stream);
+int ed3dgs_integrate_view_probe(
+    int PN, int P, int R, int width, int height, const char *geometry_buffer, const char *binning_buffer,
+    const char *image_buffer, const char *workspace, ed3dgs_alloc_fn point_alloc, void *point_user, const float *points3D,
+    const float *viewmatrix, float tan_fovx, float tan_fovy, const float *invraycov, const unsigned char *condition,
+    const float *out_color, float *point_count, float *out_alpha_integrated, float *out_color_integrated,
+    float *out_coordinate2d, float *out_sdf, int debug, void *stream);
+
+/*
+ * Marching tetrahedra (utils/tetmesh.py:_unbatched_marching_tetrahedra, one batch entry), in two calls because the
+ * output sizes are data-dependent.  A vertex is inside when sdf > 0 (0 and NaN are outside); a tet is valid when 1-3 of
+ * its vertices are inside.  Output vertex k is the k-th crossing edge (one end inside) in lexicographic (min, max) order;
+ * faces are the one-triangle tets in tet order, then the two-triangle tets in tet order, corners from the reference's
+ * triangle table.  tets [T,4] int32 (tets_int64 = 0) or int64, every index in [0, N) (else ED3DGS_ERR_INVALID), T <= 2^29.
+ *
+ * ed3dgs_tetmesh_count: tet_ws >= ed3dgs_tetmesh_tet_bytes(T) device bytes; `edge_alloc` is asked for
+ * ed3dgs_tetmesh_edge_bytes(S) bytes.  Writes the HOST array counts = {E vertices, n1 one-triangle tets, n2 two-triangle
+ * tets, S crossing-edge slots}; synchronises the stream twice (S sizes the edge sort, E the outputs).
+ * ed3dgs_tetmesh_emit: the same tets / sdf and both workspaces unchanged, plus vertices [N,3], scales [N] float32.
+ * Writes out_verts [E,2,3], out_sdf [E,2], out_scales [E,2] (the endpoints' positions, sdf and scales), out_faces
+ * [n1 + 2 n2, 3] int64 and out_ids [E,2] int64 (min, max).  Asynchronous.
+ */
+size_t ed3dgs_tetmesh_tet_bytes(int T);
+size_t ed3dgs_tetmesh_edge_bytes(int S);
+int ed3dgs_tetmesh_count(int N, int T, const void *tets, int tets_int64, const float *sdf, char *tet_ws, size_t tet_ws_bytes,
+                         ed3dgs_alloc_fn edge_alloc, void *edge_user, long long counts[4], void *stream);
+int ed3dgs_tetmesh_emit(int N, int T, const void *tets, int tets_int64, const float *vertices, const float *sdf,
+                        const float *scales, const char *tet_ws, const char *edge_ws, const long long counts[4],
+                        float *out_verts, float *out_sdf, float *out_scales, long long *out_faces, long long *out_ids,
+                        void *stream);
+
+/*
  * simple_knn.distCUDA2 (submodules/simple-knn/simple_knn.cu:185-220, ext binding simple-knn/ext.cpp:15):
  * mean_dist2[i] = mean of the squared distances from point i to its 3 nearest OTHER points (exact k-NN; a slot with no
  * neighbour counts FLT_MAX, as in the reference, so clouds of fewer than 4 points give huge / infinite values).
